@@ -3,6 +3,7 @@
 rollout + update (BASELINE.json configs[1]; per GPU when sharded).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--compute f32|bf16]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one full `ppo_step` iteration (rollout -> n_epochs x n_minibatches
@@ -13,17 +14,24 @@ per iteration — the read of the iteration's metrics, the counterpart of the re
 i+1 is enqueued before the host waits for iteration i, as `train_ppo` does when no
 callback is due).
 
-Timing: W untimed warm-up steps, then windows of EXACTLY K steps, each
-bracketed by barrier + device synchronise on both sides and reduced with MAX over ranks;
-the window is repeated until >= 1 s has been timed.  `value` = env-steps of one window /
-the MEDIAN window time; `iteration_ms` = p10 / p50 / p90 of the per-iteration wall times
-(host sync to host sync) over all windows.  `back_to_back` is the same graph replayed K
-times with no host read in between (round 1's definition), and `train_ppo` is
-`throughput/train_sps` as the drop-in entry point itself reports it on this box.
+Timing: W untimed warm-up steps, then ONE window of exactly K steps,
+bracketed by barrier + device synchronise on both sides and reduced with MAX over ranks.
+`value` = env-steps of the window / its time, `ms_per_step` = its time / K;
+`iteration_ms` = p10 / p50 / p90 of the per-iteration wall times (host sync to host sync).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
-`roofline` (dominant kernel, timed live with HIP events on the launch stream)
-and `cpu_baseline` (the CPU oracle timed on this box's host cores, N=1 only).
+--dump-outputs DIR writes what the timed path hands its caller after its last timed step
+(the training state and the metrics `ppo_step` returns; rank 0's under N > 1) as
+DIR/<name>.npy.  The inputs are seeded, so the same arguments give the same inputs.
+
+A plain run measures the headline and nothing else.  --full adds, after it: `windows`
+(K-step windows repeated until >= --min-timed-seconds are timed, median window),
+`back_to_back` (the same graph replayed K times with no host read in between, round 1's
+definition), `roofline` (dominant kernel, timed live with HIP events on the launch stream),
+`train_ppo` (`throughput/train_sps` as the drop-in entry point itself reports it on this
+box), `configs` (C3 / C4) and `cpu_baseline` (the CPU oracle on this box's host cores);
+the last three at N = 1 only.
+
+Prints ONE JSON line on rank 0 (contract in the task statement).
 """
 from __future__ import annotations
 
@@ -363,6 +371,73 @@ def _pct(xs, q):
     return xs[lo] + (xs[hi] - xs[lo]) * (pos - lo)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _named_leaves(prefix: str, x, out: dict) -> None:
+    """Tensors and numbers of a pytree (dataclasses, dicts, lists, tuples) by dotted path."""
+    import dataclasses
+
+    if isinstance(x, torch.Tensor):
+        out[prefix] = x
+    elif dataclasses.is_dataclass(x) and not isinstance(x, type):
+        for f in dataclasses.fields(x):
+            _named_leaves(f"{prefix}.{f.name}", getattr(x, f.name), out)
+    elif isinstance(x, dict):
+        for k in sorted(x, key=str):
+            _named_leaves(f"{prefix}.{k}", x[k], out)
+    elif isinstance(x, (list, tuple)):
+        for i, v in enumerate(x):
+            _named_leaves(f"{prefix}.{i}", v, out)
+    elif isinstance(x, (bool, int, float)):
+        out[prefix] = torch.tensor(x, dtype=torch.float64)
+
+
+def dump_outputs(out_dir: str, ts, metrics: dict) -> int:
+    """What `ppo_step` hands its caller — the training state (parameters, the modules'
+    variables such as the normaliser statistics, Adam's arenas, network / env states, rng
+    key, step count) and the iteration's metrics — as `out_dir/<name>.npy`.  float64,
+    bool and integer leaves are stored as float64 (64-bit integers such as the rng key as
+    their exact [high, low] 32-bit halves, one more trailing axis), every other float as
+    float32.  Returns the bytes written."""
+    import re
+
+    import numpy as np
+
+    from nnx_ppo_amd.algorithms.checkpointing import _named_variables
+    from nnx_ppo_amd.algorithms.graph import _tensor_fields
+
+    leaves: dict = {}
+    for n, p in ts.networks.named_parameters():
+        _named_leaves(f"params.{n}", p.data, leaves)
+    for n, v in _named_variables(ts.networks):
+        _named_leaves(f"variables.{n}", v.value, leaves)
+    for n in ("m", "v", "step"):
+        _named_leaves(f"optimizer.{n}", getattr(ts.optimizer, n), leaves)
+    for n in _tensor_fields(ts):
+        _named_leaves(n, getattr(ts, n), leaves)
+    _named_leaves("metrics", metrics, leaves)
+
+    arrays = {}
+    for name, t in leaves.items():
+        t = t.detach().cpu()
+        if t.dtype == torch.int64:
+            t = torch.stack([t >> 32, t & 0xFFFFFFFF], dim=-1)
+        wide = t.dtype == torch.float64 or not t.is_floating_point()
+        fname = re.sub(r"[^A-Za-z0-9_.-]", "_", name)
+        if fname in arrays:
+            raise SystemExit(f"[bench] --dump-outputs: two outputs map to {fname}.npy")
+        arrays[fname] = t.to(torch.float64 if wide else torch.float32).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"[bench] --dump-outputs: {total} bytes > {DUMP_MAX_BYTES}")
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for fname, a in arrays.items():
+        np.save(d / f"{fname}.npy", a)
+    return total
+
+
 def train_ppo_throughput(device, compute: str, iterations: int = 45):
     """`throughput/train_sps` as the drop-in `train_ppo` reports it (fresh state, same
     workload): median over the iterations after the eager first one and the capture."""
@@ -543,12 +618,20 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the training state and metrics of the last timed step as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: repeated windows, back-to-back replays, "
+                         "roofline, train_ppo, C3 / C4 and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU oracle's timing")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short C3 / C4 windows reported under `configs`")
+                    help="--full: skip the short C3 / C4 windows reported under `configs`")
     ap.add_argument("--no-train-ppo", action="store_true",
-                    help="skip the cross-check run of train_ppo itself")
-    ap.add_argument("--min-timed-seconds", type=float, default=1.0)
+                    help="--full: skip the cross-check run of train_ppo itself")
+    ap.add_argument("--min-timed-seconds", type=float, default=1.0,
+                    help="--full: time repeated windows until this many seconds")
     ap.add_argument("--compute", choices=["f32", "bf16"], default="bf16",
                     help="MFMA path of the Dense layers (BASELINE configs[1] is bf16)")
     ap.add_argument("--eager", action="store_true",
@@ -641,38 +724,36 @@ def main():
     _log(f"built; warm-up {warm} iterations (1 eager, 1 recorded, rest replayed)")
     run_window(warm)
     _log("warm-up done")
-    # size the repetition count from one untimed window
-    est = run_window(args.steps)
-    if world > 1:
-        # every rank must run the SAME number of windows (each window holds two barriers): the
-        # count comes from the slowest rank's estimate, not from each rank's own clock
+
+    def max_over_ranks(xs: list) -> list:
+        if world == 1:
+            return list(xs)
         import torch.distributed as dist
 
-        et = torch.tensor([est], dtype=torch.float64, device=device)
+        t = torch.tensor(xs, dtype=torch.float64, device=device)
         if backend != "nccl":
-            et = et.cpu()
-        dist.all_reduce(et, op=dist.ReduceOp.MAX)
-        est = float(et.cpu()[0])
-    reps = max(1, min(200, int(args.min_timed_seconds / max(est, 1e-6)) + 1))
-    _log(f"one window of {args.steps} iterations = {est * 1e3:.1f} ms; timing {reps} windows")
-    windows, iter_ms = [], []
-    for _ in range(reps):
-        stamps = [time.perf_counter()]
-        windows.append(run_window(args.steps, stamps))
+            t = t.cpu()
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        return [float(x) for x in t.cpu()]
+
+    def iteration_ms(stamps) -> list:
         # the first interval holds the window's launch of its first iteration; the
         # steady-state intervals are host sync to host sync
-        iter_ms += [(b - a) * 1e3 for a, b in zip(stamps[1:-1], stamps[2:])]
-    metrics = run_window.metrics
-    own_windows = list(windows)  # this rank's own clock, before the MAX over ranks
-    wt = torch.tensor(windows, dtype=torch.float64, device=device)
-    if world > 1:
-        import torch.distributed as dist
+        return [(b - a) * 1e3 for a, b in zip(stamps[1:-1], stamps[2:])]
 
-        if backend != "nccl":
-            wt = wt.cpu()
-        dist.all_reduce(wt, op=dist.ReduceOp.MAX)
-    windows = [float(x) for x in wt.cpu()]
-    elapsed = _pct(windows, 0.5)
+    def pcts(xs, scale, nd):
+        return {f"p{q}": round(_pct(xs, q / 100) * scale, nd) for q in (10, 50, 90)}
+
+    # the headline: ONE window of exactly `steps` iterations
+    stamps = [time.perf_counter()]
+    own = run_window(args.steps, stamps)  # this rank's own clock, before the MAX over ranks
+    metrics = run_window.metrics
+    iter_ms = iteration_ms(stamps)
+    elapsed = max_over_ranks([own])[0]
+    _log(f"timed: {args.steps} iterations in {elapsed * 1e3:.2f} ms")
+    if args.dump_outputs and rank == 0:
+        nbytes = dump_outputs(args.dump_outputs, runner.state, metrics)
+        _log(f"outputs of the last timed step ({nbytes / 2**20:.2f} MiB) -> {args.dump_outputs}")
     # one line per rank: what it ran on, how its exchanges travel, its own clock
     props = torch.cuda.get_device_properties(device)
     comm = None
@@ -687,30 +768,62 @@ def main():
         "dist_backend": None if world == 1 else dist.get_backend(),
         "transport": transport, "oneshot_self_check": oneshot_check,
         "oneshot_timeouts": None if comm is None else comm.status()[1],
-        "ms_per_step_own_clock": round(_pct(own_windows, 0.5) / args.steps * 1e3, 4),
-        "iteration_ms_p50_own_clock": round(_pct(iter_ms, 0.5), 4),
+        "ms_per_step_own_clock": round(own / args.steps * 1e3, 4),
+        "iteration_ms_p50_own_clock": round(_pct(iter_ms, 0.5), 4) if iter_ms else None,
     }
     ranks = [me]
     if world > 1:
         ranks = [None] * world
         dist.all_gather_object(ranks, me)
 
-    _log(f"timed: median window {elapsed * 1e3:.2f} ms")
-    # the same graph replayed back to back, no host read in between (round 1's number)
-    b2b = None
-    if runner._graph is not None:
-        barrier()
-        t0 = time.perf_counter()
-        with torch.cuda.stream(runner.stream):
-            for _ in range(args.steps):
-                runner._graph()
-        barrier()
-        b2b = time.perf_counter() - t0
+    full = {}
+    if args.full:
+        # windows of `steps` iterations repeated until --min-timed-seconds, sized from one
+        # untimed window.  Every rank must run the SAME number of windows (each window holds
+        # two barriers): the count comes from the slowest rank's estimate, not from each
+        # rank's own clock
+        est = max_over_ranks([run_window(args.steps)])[0]
+        reps = max(1, min(200, int(args.min_timed_seconds / max(est, 1e-6)) + 1))
+        _log(f"one window of {args.steps} iterations = {est * 1e3:.1f} ms; timing {reps} windows")
+        windows, w_iter_ms = [], []
+        for _ in range(reps):
+            st = [time.perf_counter()]
+            windows.append(run_window(args.steps, st))
+            w_iter_ms += iteration_ms(st)
+        windows = max_over_ranks(windows)
+        med = _pct(windows, 0.5)
+        total_env_steps = world * N_ENVS * T * args.steps
+        full["windows"] = {
+            "definition": "the headline's window repeated until >= min_timed_seconds are "
+                          "timed; value from the median window",
+            "value": round(total_env_steps / med, 1),
+            "ms_per_step": round(med / args.steps * 1e3, 3),
+            "windows": len(windows), "timed_s": round(sum(windows), 3),
+            "window_ms": pcts(windows, 1e3, 3),
+            "iteration_ms": dict(pcts(w_iter_ms, 1, 4), n=len(w_iter_ms)),
+        }
+        _log(f"windows: median {med * 1e3:.2f} ms")
+        # the same graph replayed back to back, no host read in between (round 1's number)
+        full["back_to_back"] = None
+        if runner._graph is not None:
+            barrier()
+            t0 = time.perf_counter()
+            with torch.cuda.stream(runner.stream):
+                for _ in range(args.steps):
+                    runner._graph()
+            barrier()
+            b2b = time.perf_counter() - t0
+            full["back_to_back"] = {
+                "value": round(total_env_steps / b2b, 1),
+                "ms_per_step": round(b2b / args.steps * 1e3, 3),
+                "note": "K graph replays enqueued with no host read, one final synchronise "
+                        "(rank 0's clock)"}
 
-    # instrumented iteration on every rank (collectives must match), reported by rank 0
-    _log("instrumented iteration (HIP events around every C-ABI call)")
-    ts, roof, per_kernel = roofline_of_dominant_kernel(env, runner.state)
-    _log("roofline done")
+        # instrumented iteration on every rank (collectives must match), reported by rank 0
+        _log("instrumented iteration (HIP events around every C-ABI call)")
+        ts, full["roofline"], full["kernels_ms_per_iter"] = roofline_of_dominant_kernel(
+            env, runner.state)
+        _log("roofline done")
 
     if rank == 0:
         total_env_steps = world * N_ENVS * T * args.steps
@@ -743,34 +856,22 @@ def main():
             },
             "timing": {
                 "definition": "train_ppo's loop: one graph launch + one host sync (metric "
-                              "read) per iteration; window = exactly `steps` iterations "
-                              "between barrier+synchronize pairs, MAX over ranks; value from "
-                              "the median window",
-                "windows": len(windows), "timed_s": round(sum(windows), 3),
-                "window_ms": {"p10": round(_pct(windows, 0.1) * 1e3, 3),
-                              "p50": round(_pct(windows, 0.5) * 1e3, 3),
-                              "p90": round(_pct(windows, 0.9) * 1e3, 3)},
-                "iteration_ms": {"p10": round(_pct(iter_ms, 0.1), 4),
-                                 "p50": round(_pct(iter_ms, 0.5), 4),
-                                 "p90": round(_pct(iter_ms, 0.9), 4), "n": len(iter_ms)},
+                              "read) per iteration; ONE window of exactly `steps` iterations "
+                              "between barrier+synchronize pairs, MAX over ranks",
+                "windows": 1, "timed_s": round(elapsed, 4),
+                "iteration_ms": dict(pcts(iter_ms, 1, 4), n=len(iter_ms)) if iter_ms else None,
             },
-            "back_to_back": None if b2b is None else {
-                "value": round(total_env_steps / b2b, 1),
-                "ms_per_step": round(b2b / args.steps * 1e3, 3),
-                "note": "K graph replays enqueued with no host read, one final synchronise "
-                        "(rank 0's clock)"},
             "launch_mode": runner.launch_mode,
-            "roofline": roof,
-            "kernels_ms_per_iter": per_kernel,
             "final_losses": {k: float(v) for k, v in metrics.items() if k.startswith("losses/")},
+            **full,
         }
-        if world == 1 and not args.no_train_ppo and not args.eager:
+        if args.full and world == 1 and not args.no_train_ppo and not args.eager:
             _log("train_ppo cross-check")
             line["train_ppo"] = train_ppo_throughput(device, args.compute)
-        if world == 1 and not args.no_other_configs and not args.eager:
+        if args.full and world == 1 and not args.no_other_configs and not args.eager:
             _log("other configs (C3, C4): short windows, same timing definition")
             line["configs"] = other_configs(device, args.compute)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             _log("cpu baseline (oracle on the host cores)")
             line["cpu_baseline"] = cpu_baseline()
         _log("done")

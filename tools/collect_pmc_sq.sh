@@ -9,7 +9,7 @@ root=$(pwd)
 out=$root/gpurun_out/${tag}_sq
 mkdir -p "$out"
 export TMPDIR=/tmp
-cmd="python3 bench.py --no-cpu-baseline --no-train-ppo --steps 3 --warmup 1"
+cmd="python3 bench.py --full --no-cpu-baseline --no-train-ppo --steps 3 --warmup 1"
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SMEM \
     SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR -d "$out/p1" -o p1 --output-format csv -- $cmd > /dev/null
 echo "pass 1 done"

@@ -17,19 +17,19 @@ out=$root/gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d "$out/stats" -o stats --output-format csv -- \
-    python3 bench.py --no-cpu-baseline --no-other-configs > "$out/bench_under_rocprof.json"
+    python3 bench.py --full --no-cpu-baseline --no-other-configs > "$out/bench_under_rocprof.json"
 echo "stats done"
 rocprofv3 --pmc FETCH_SIZE -d "$out/fetch" -o fetch --output-format csv -- \
-    python3 bench.py --no-cpu-baseline --no-other-configs --steps 3 --warmup 1 > /dev/null
+    python3 bench.py --full --no-cpu-baseline --no-other-configs --steps 3 --warmup 1 > /dev/null
 echo "fetch done"
 rocprofv3 --pmc WRITE_SIZE -d "$out/write" -o write --output-format csv -- \
-    python3 bench.py --no-cpu-baseline --no-other-configs --steps 3 --warmup 1 > /dev/null
+    python3 bench.py --full --no-cpu-baseline --no-other-configs --steps 3 --warmup 1 > /dev/null
 echo "write done"
 python3 tools/pmc_summary.py "$out/fetch" "$out/write" "$out/pmc_traffic.json"
 cp "$out/pmc_traffic.json" "$root/profiles/${round}_pmc_traffic.json"
 cp "$(find "$out/stats" -name '*kernel_stats.csv' | head -1)" "$out/kernel_stats.csv"
 # the raw traces are large; keep the summaries only
 rm -rf "$out/stats" "$out/fetch" "$out/write"
-python3 bench.py > "$out/bench.json"
+python3 bench.py --full > "$out/bench.json"
 echo "bench done"
 cat "$out/bench.json"

@@ -7,7 +7,7 @@ set -eo pipefail
 port=${1:-29511}
 MIPPO_DIST_BACKEND=gloo MIPPO_SINGLE_DEVICE=1 timeout -k 10 400 python3 -m torch.distributed.run \
   --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port "$port" \
-  bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline --no-train-ppo \
+  bench.py --gpus 2 --steps 10 --warmup 3 --full --no-cpu-baseline --no-train-ppo \
   > gpurun_out/bench_n2.json 2> gpurun_out/bench_n2.err || { tail -20 gpurun_out/bench_n2.err; exit 1; }
 python3 - <<'P'
 import json
