@@ -943,6 +943,43 @@ int mi_adam_step_allreduce_f32(void* comm, float* params, float* grads, float* m
  * summed into this rank's gradient chunk before it is pushed — mi_adam_step_slabs_f32's sums
  * in the same order — so a sharded gradient step is forward, backward, dW and this launch.) */
 
+/* ---- variational bottlenecks ------------------------------------------- */
+
+/* VariationalBottleneck / AR1VariationalBottleneck over a whole sequence,
+ * `nnx_ppo/networks/variational.py:35-81` (VB `__call__`) and `137-202` (AR1 `__call__`),
+ * T steps scanned as `ppo.py:411-431` does, `done[t]` resetting the carry after step t
+ * (`variational.py:210-216`: keys kept, last_z <- NaN).  x [T, B, 2L] = [mean | log_std]:
+ *   sigma = softplus(log_std) + min_std, eps = unit_normal(key, (L,)), z = mean + sigma eps
+ *   KL = 1/2 sum_l (mean^2 + sigma^2 - 2 ln sigma - 1)                  (`:63-67`, `:170-174`)
+ *   l2 = mean_l (z - p~)^2, p~ = isnan(p) ? z : p  (ar1 != 0 only)      (`:176-181`)
+ *   reg = kl_weight KL + ar1_weight l2; next key = split(key)[0]         (`:69`, `:185`)
+ * key0 [B] int64 keys (nnx_ppo_amd/random.py scheme), last_z0 [B, L] (ar1; NaN = no AR1
+ * term), done [T, B] or NULL.  Outputs z [T, B, L], reg [T, B], key_out [B] and (ar1)
+ * last_z_out [B, L]: the carry after step T - 1 and its reset; nullable: eps [T, B, L] (what
+ * mi_vb_seq_bwd_f32 reads), kl / l2 [T, B] (the `kl_divergence` / `l2_diff` metrics), sigma
+ * [T, B, L].  1 <= L <= mi_vb_max_latent().  Step t of a row has the bits of the same row
+ * evaluated alone at T = 1 from step t's carry. */
+int mi_vb_seq_fwd_f32(const float* x, const int64_t* key0, const float* last_z0,
+                      const uint8_t* done, float* z, float* eps, float* reg, float* kl,
+                      float* l2, float* sigma, int64_t* key_out, float* last_z_out, int64_t T,
+                      int64_t B, int64_t L, float kl_weight, float ar1_weight, float min_std,
+                      int ar1, mi_stream_t stream);
+
+/* Gradient of mi_vb_seq_fwd_f32 (`nnx.grad` through `variational.py:137-202` inside the
+ * loss scan, `ppo.py:415-431`): g_x [T, B, 2L] from g_z [T, B, L] (nullable: zero) and the
+ * scalar g_reg (d loss / d reg[t, b]), with the forward's x, eps and (ar1) z, last_z0, done:
+ *   a_t = g_reg ar1_weight (2/L) (z_t - p_t) [p_t valid]
+ *   dz_t = g_z_t + a_t - bptt a_{t+1} (a_{t+1} within the sequence; `:159-160` stop_gradient)
+ *   dmean = dz_t + g_reg kl_weight mean,  dsigma = dz_t eps + g_reg kl_weight (sigma - 1/sigma)
+ *   dlog_std = dsigma sigmoid(log_std).  Elementwise, no atomics. */
+int mi_vb_seq_bwd_f32(const float* x, const float* eps, const float* z, const float* last_z0,
+                      const uint8_t* done, const float* g_z, float g_reg, float* g_x, int64_t T,
+                      int64_t B, int64_t L, float kl_weight, float ar1_weight, float min_std,
+                      int ar1, int bptt, mi_stream_t stream);
+
+/* Largest latent size L the two calls above accept (512). */
+int mi_vb_max_latent(void);
+
 #ifdef __cplusplus
 }
 #endif

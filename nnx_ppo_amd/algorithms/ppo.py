@@ -677,6 +677,10 @@ def new_training_state(
         for m in networks.modules():
             if hasattr(m, "seed") and hasattr(m, "advance_rng"):
                 m.seed = (m.seed + 0x9E3779B97F4A7C15 * (1 + parallel.rank())) & (2**63 - 1)
+            # other per-env noise sources (variational bottlenecks) fold the rank themselves
+            fold_rank = getattr(m, "fold_rank", None)
+            if fold_rank is not None:
+                fold_rank(parallel.rank())
     ks = rnd.split(key)
     key, training_key = ks[0], ks[1]
     env_init_keys = rnd.split(key, n_envs)

@@ -1999,3 +1999,68 @@ def lstm_seq_bwd(g_h, gates, c_prev, w_h, done, mfma: bool = False, want_dinit: 
         dinit = part.sum(dim=0)  # block order: deterministic
         return da, dinit[0], dinit[1]
     return da
+
+
+# ------------------------------------------------- variational bottlenecks
+def vb_max_latent() -> int:
+    return int(lib().mi_vb_max_latent())
+
+
+def vb_seq_fwd(x, key0, last_z0, done, *, kl_weight: float, ar1_weight: float, min_std: float,
+               ar1: bool, want_eps: bool = True, want_metrics: bool = False,
+               want_sigma: bool = False):
+    """x [T, B, 2L], key0 [B] int64, last_z0 [B, L] (AR1) or None, done [T, B] or None ->
+    dict(z [T,B,L], eps [T,B,L] | None, reg [T,B], kl / l2 [T,B] | None, sigma [T,B,L] | None,
+    keys [B], last_z [B,L] | None) (reference variational.py:35-81, 137-202)."""
+    _need(x.dim() == 3 and x.shape[2] % 2 == 0, f"vb_seq_fwd: x must be [T, B, 2L], got "
+          f"{tuple(x.shape)}")
+    T, B, L2 = x.shape
+    L = L2 // 2
+    _need(key0.shape == (B,) and key0.dtype == i64, "vb_seq_fwd: keys must be int64 [B]")
+    if ar1:
+        _need(last_z0 is not None and last_z0.shape == (B, L),
+              f"vb_seq_fwd: last_z must be [{B}, {L}]")
+    else:
+        _need(last_z0 is None, "vb_seq_fwd: last_z belongs to the AR1 form")
+    d = None if done is None else _as_u8(done)
+    if d is not None:
+        _need(d.shape == (T, B), "vb_seq_fwd: done must be [T, B]")
+    dev = x.device
+    mk = lambda *s: torch.empty(*s, dtype=f32, device=dev)
+    z = mk(T, B, L)
+    eps = mk(T, B, L) if want_eps else None
+    reg = mk(T, B)
+    kl = mk(T, B) if want_metrics else None
+    l2 = mk(T, B) if (want_metrics and ar1) else None
+    sigma = mk(T, B, L) if want_sigma else None
+    keys = torch.empty(B, dtype=i64, device=dev)
+    last_z = mk(B, L) if ar1 else None
+    check(lib().mi_vb_seq_fwd_f32(
+        ptr(x, f32), ptr(key0, i64), ptr(last_z0, f32), ptr(d), ptr(z, f32), ptr(eps, f32),
+        ptr(reg, f32), ptr(kl, f32), ptr(l2, f32), ptr(sigma, f32), ptr(keys, i64),
+        ptr(last_z, f32), T, B, L, float(kl_weight), float(ar1_weight), float(min_std),
+        int(bool(ar1)), stream()), "mi_vb_seq_fwd_f32")
+    return dict(z=z, eps=eps, reg=reg, kl=kl, l2=l2, sigma=sigma, keys=keys, last_z=last_z)
+
+
+def vb_seq_bwd(x, eps, z, last_z0, done, g_z, g_reg: float, *, kl_weight: float,
+               ar1_weight: float, min_std: float, ar1: bool, bptt: bool):
+    """g_x [T, B, 2L] of `vb_seq_fwd` from g_z [T, B, L] (None: zero) and the scalar g_reg."""
+    T, B, L2 = x.shape
+    L = L2 // 2
+    _need(eps.shape == (T, B, L), "vb_seq_bwd: eps must be [T, B, L]")
+    if ar1:
+        _need(z is not None and z.shape == (T, B, L), "vb_seq_bwd: z must be [T, B, L]")
+        _need(last_z0 is None or last_z0.shape == (B, L), "vb_seq_bwd: last_z must be [B, L]")
+    if g_z is not None:
+        _need(g_z.shape == (T, B, L), "vb_seq_bwd: g_z must be [T, B, L]")
+    d = None if done is None else _as_u8(done)
+    if d is not None:
+        _need(d.shape == (T, B), "vb_seq_bwd: done must be [T, B]")
+    g_x = torch.empty_like(x)
+    check(lib().mi_vb_seq_bwd_f32(
+        ptr(x, f32), ptr(eps, f32), ptr(z if ar1 else None, f32),
+        ptr(last_z0 if ar1 else None, f32), ptr(d), ptr(g_z, f32), float(g_reg), ptr(g_x, f32),
+        T, B, L, float(kl_weight), float(ar1_weight), float(min_std), int(bool(ar1)),
+        int(bool(bptt)), stream()), "mi_vb_seq_bwd_f32")
+    return g_x
