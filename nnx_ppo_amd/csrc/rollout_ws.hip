@@ -109,7 +109,11 @@ __device__ __forceinline__ void ws_rollout_body(const WsChain& c, const RolloutE
   const int K0 = c.K0, N_out = c.N_out;
   const int64_t ntiles = (N + ROWS - 1) / ROWS;
 
-  constexpr int IN_PT = (ROWS * 32 + kWsThreads - 1) / kWsThreads;  // K0 <= 32
+  // Observation element e = row * K0 + k of the tile is staged by thread e % kWsThreads in slot
+  // e / kWsThreads (K0 <= 32).  The slot holding a row's k = 0 element owns that row's env
+  // state: it computes and publishes the row's next (key, count, counter, done).  Ownership
+  // is per slot, not per thread: at K0 = 32 thread 32j stages k = 0 of rows j and j + 16.
+  constexpr int IN_PT = (ROWS * 32 + kWsThreads - 1) / kWsThreads;
   const int nel = ROWS * K0;
   const float rcpK0 = 1.0f / (float)K0;
 
@@ -193,13 +197,18 @@ __device__ __forceinline__ void ws_rollout_body(const WsChain& c, const RolloutE
       // env step of the element's row, in registers (nothing of step t + 1 is published before
       // the barrier below: every thread still reads the state of step t)
       float xnext[IN_PT];
-      int64_t nkey = 0, ncount = 0, ncounter = 0;
-      bool owner = false, m_row = false;
-      int owner_row = 0;
+      // the next state of the row whose k = 0 element slot u stages (owner[u]): one slot per
+      // staged element, since a thread can stage the k = 0 elements of two rows (K0 = 32)
+      int64_t nkey[IN_PT], ncount[IN_PT], ncounter[IN_PT];
+      bool owner[IN_PT], m_row[IN_PT];
+      int owner_row[IN_PT];
 #pragma unroll
       for (int u = 0; u < IN_PT; ++u) {
         const int e = tid + u * kWsThreads;
         xnext[u] = 0.0f;
+        owner[u] = m_row[u] = false;
+        owner_row[u] = 0;
+        nkey[u] = ncount[u] = ncounter[u] = 0;
         if (e < nel) {
           const int row = (int)(((float)e + 0.5f) * rcpK0);
           const int k = e - row * K0;
@@ -243,21 +252,31 @@ __device__ __forceinline__ void ws_rollout_body(const WsChain& c, const RolloutE
             }
             xnext[u] = nobs;
             if (k == 0) {
-              owner = true;
-              owner_row = row;
-              nkey = k2;
-              ncount = s2;
-              ncounter = c2;
-              m_row = m;
+              owner[u] = true;
+              owner_row[u] = row;
+              nkey[u] = k2;
+              ncount[u] = s2;
+              ncounter[u] = c2;
+              m_row[u] = m;
             }
           }
         }
       }
       __syncthreads();  // bufX staged; every read of the step-t state is done
-      if (owner) {
-        s_key[owner_row] = nkey;
-        s_count[owner_row] = ncount;
-        s_counter[owner_row] = ncounter;
+#pragma unroll
+      for (int u = 0; u < IN_PT; ++u) {
+        if (owner[u]) {
+          s_key[owner_row[u]] = nkey[u];
+          s_count[owner_row[u]] = ncount[u];
+          s_counter[owner_row[u]] = ncounter[u];
+          if (SAMP && t == T - 1) {  // the carried state (reset select applied)
+            const int64_t gi = i0 + owner_row[u];
+            env.key_out[gi] = nkey[u];
+            env.count_out[gi] = ncount[u];
+            env.counter_out[gi] = ncounter[u];
+            env.reward_out[gi] = m_row[u] ? 0.0f : 1.0f;
+          }
+        }
       }
 
       f32x4 acc[RTW][TPW];
@@ -377,13 +396,6 @@ __device__ __forceinline__ void ws_rollout_body(const WsChain& c, const RolloutE
             if (gi < N) env.obs_out[gi * K0 + (e - row * K0)] = xin[u];
           }
         }
-        if (owner) {
-          const int64_t gi = i0 + owner_row;
-          env.key_out[gi] = nkey;
-          env.count_out[gi] = ncount;
-          env.counter_out[gi] = ncounter;
-          env.reward_out[gi] = m_row ? 0.0f : 1.0f;
-        }
       }
     }
   }
@@ -459,6 +471,7 @@ __device__ __forceinline__ void ws_gru_rollout_body(const WsChain& c, const GruR
   const int T = env.T;
   const int K0 = c.K0, N_out = c.N_out;
   const int64_t ntiles = (N + ROWS - 1) / ROWS;
+  // staging and row ownership per slot, as in ws_rollout_body (K0 <= 32)
   constexpr int IN_PT = (ROWS * 32 + kWsThreads - 1) / kWsThreads;
   constexpr int H_CH = ROWS * (H / 4);
   constexpr int H_PT = (H_CH + kWsThreads - 1) / kWsThreads;
@@ -521,7 +534,7 @@ __device__ __forceinline__ void ws_gru_rollout_body(const WsChain& c, const GruR
       s_key[tid] = env.key[gi];
       s_count[tid] = env.count[gi];
       s_counter[tid] = env.counter[gi];
-      s_done[tid] = 0;  // rows beyond N never get an owner
+      s_done[tid] = 0;  // rows beyond N never get an owning slot: their flag stays 0
     }
     float xin[IN_PT];
 #pragma unroll
@@ -559,13 +572,17 @@ __device__ __forceinline__ void ws_gru_rollout_body(const WsChain& c, const GruR
     for (int t = 0; t < T; ++t) {
       const int64_t tN = (int64_t)t * N;
       float xnext[IN_PT];
-      int64_t nkey = 0, ncount = 0, ncounter = 0;
-      bool owner = false, m_row = false;
-      int owner_row = 0;
+      // one slot per staged element, as in ws_rollout_body
+      int64_t nkey[IN_PT], ncount[IN_PT], ncounter[IN_PT];
+      bool owner[IN_PT], m_row[IN_PT];
+      int owner_row[IN_PT];
 #pragma unroll
       for (int u = 0; u < IN_PT; ++u) {
         const int e = tid + u * kWsThreads;
         xnext[u] = 0.0f;
+        owner[u] = m_row[u] = false;
+        owner_row[u] = 0;
+        nkey[u] = ncount[u] = ncounter[u] = 0;
         if (e < nel) {
           const int row = (int)(((float)e + 0.5f) * rcpK0);
           const int k = e - row * K0;
@@ -604,22 +621,32 @@ __device__ __forceinline__ void ws_gru_rollout_body(const WsChain& c, const GruR
             }
             xnext[u] = nobs;
             if (k == 0) {
-              owner = true;
-              owner_row = row;
-              nkey = k2;
-              ncount = s2;
-              ncounter = c2;
-              m_row = m;
+              owner[u] = true;
+              owner_row[u] = row;
+              nkey[u] = k2;
+              ncount[u] = s2;
+              ncounter[u] = c2;
+              m_row[u] = m;
             }
           }
         }
       }
       __syncthreads();  // bufX and (first step) bufA staged; the step-t state has been read
-      if (owner) {
-        s_key[owner_row] = nkey;
-        s_count[owner_row] = ncount;
-        s_counter[owner_row] = ncounter;
-        s_done[owner_row] = m_row ? 1 : 0;
+#pragma unroll
+      for (int u = 0; u < IN_PT; ++u) {
+        if (owner[u]) {
+          s_key[owner_row[u]] = nkey[u];
+          s_count[owner_row[u]] = ncount[u];
+          s_counter[owner_row[u]] = ncounter[u];
+          s_done[owner_row[u]] = m_row[u] ? 1 : 0;
+          if (t == T - 1) {  // the carried env state (reset select applied)
+            const int64_t gi = i0 + owner_row[u];
+            env.key_out[gi] = nkey[u];
+            env.count_out[gi] = ncount[u];
+            env.counter_out[gi] = ncounter[u];
+            env.reward_out[gi] = m_row[u] ? 0.0f : 1.0f;
+          }
+        }
       }
       // ---- Dense(obs -> H, relu) -------------------------------------------------------------
 #pragma unroll
@@ -726,13 +753,6 @@ __device__ __forceinline__ void ws_gru_rollout_body(const WsChain& c, const GruR
             const int64_t gi = i0 + row;
             if (gi < N) env.obs_out[gi * K0 + (e - row * K0)] = xin[u];
           }
-        }
-        if (owner) {
-          const int64_t gi = i0 + owner_row;
-          env.key_out[gi] = nkey;
-          env.count_out[gi] = ncount;
-          env.counter_out[gi] = ncounter;
-          env.reward_out[gi] = m_row ? 0.0f : 1.0f;
         }
 #pragma unroll
         for (int r = 0; r < RTW; ++r) {
